@@ -13,7 +13,7 @@ RCCL all-reduce of the 8 KB fp16 O-projection partial closes each layer; total w
 scaling is "strong".  Inputs are synthetic (seeded randn*0.1 drawn on the device, random-init
 weights), resident in HBM before the timed region.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]          (N > 1 without WORLD_SIZE: spawns its N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]      (N > 1 without WORLD_SIZE: spawns its N ranks itself)
     python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N ...
 
 N > 1: every rank slices ITS heads out of the same seeded full model, so the sharded path is checkable: outside the timed
@@ -64,10 +64,16 @@ def parse():
     ap.add_argument("--leg-timeout", type=float, default=float(os.environ.get("CF_BENCH_LEG_TIMEOUT", "240")),
                     help="N > 1: seconds the optional legs (one-shot all-reduce, in-kernel publish) get before rank 0 prints "
                          "the line without them")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (every layer's out and residual_out, the "
+                         "K/V rows it wrote into the cache) as float32 DIR/<name>.npy, rank 0 only")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
 
 
-def build_layers(cfa, dev, world, rank, n_layers, S, page_size, seed=42, keep_full=0, extra_ranks=()):
+def build_layers(cfa, dev, world, rank, n_layers, S, page_size, seed=42, keep_full=0, extra_ranks=(), new_kv=None):
     """Per-layer synthetic state on the device + one PreparedLayer per layer.
 
     world > 1: rank `rank` of a head-parallel shard.  Every rank draws the SAME full layer (same seed, same generator stream)
@@ -75,6 +81,7 @@ def build_layers(cfa, dev, world, rank, n_layers, S, page_size, seed=42, keep_fu
     model and the reduced output can be checked against the unsharded kernel.  `keep_full` = how many leading layers also
     return their full tensors (rank 0's side of `tp_parity`); `extra_ranks` = further shards of those layers to build here
     (a process that plays several ranks of the shard in turn: CF_BENCH_TP > WORLD_SIZE, the one-GPU test of this path).
+    `new_kv`: a list that receives, per layer, this rank's (k_cache, v_cache, row) -- the cache row the new token is written to.
     world == 1: the slice is the whole layer -- bit-identical to what rounds 1-3 measured on."""
     from clusterfusion_amd.tp import ShardSpec, shard_kv_cache, shard_layer_weights
     g = torch.Generator(device=dev).manual_seed(seed)
@@ -123,6 +130,8 @@ def build_layers(cfa, dev, world, rank, n_layers, S, page_size, seed=42, keep_fu
         ws, wos, kcs, vcs = shard(rank, w_qkv, w_o, kc, vc)
         p = prepare(x, res, ws, wos, rms_w, kcs, vcs, perm, hq)
         layers.append(p)
+        if new_kv is not None:      # token S sits at offset S % page_size of page kv_indices[S // page_size]
+            new_kv.append((kcs, vcs, int(perm[S // page_size]) * page_size + S % page_size))
         if li < keep_full and world > 1:
             full.append(prepare(x, res, w_qkv, w_o, rms_w, kc, vc, perm, HEADS))
             others = []
@@ -714,8 +723,19 @@ def main():
     if tp % world or HEADS % tp:
         raise SystemExit(f"bench.py: a {tp}-way head shard cannot be dealt to {world} rank(s)")
     virt = list(range(rank, tp, world))      # the shard ranks this process plays (one, unless CF_BENCH_TP > WORLD_SIZE)
-    layers, full, extra = build_layers(cfa, dev, tp, rank, a.layers, S, a.page_size, keep_full=1 if tp > 1 else 0, extra_ranks=virt[1:])
+    new_kv = [] if a.dump_outputs and rank == 0 else None
+    layers, full, extra = build_layers(cfa, dev, tp, rank, a.layers, S, a.page_size, keep_full=1 if tp > 1 else 0, extra_ranks=virt[1:],
+                                       new_kv=new_kv)
     outs = [p.outputs[0] for p in layers]
+
+    def dump_outputs():
+        """What a caller of the timed path holds after its last step, per layer (rows in layer order), as float32."""
+        import numpy as np
+        arrays = {"out": [p.outputs[0].view(-1) for p in layers], "residual_out": [p.outputs[1].view(-1) for p in layers],
+                  "k_new": [kc[row] for kc, _, row in new_kv], "v_new": [vc[row] for _, vc, row in new_kv]}
+        os.makedirs(a.dump_outputs, exist_ok=True)
+        for name, rows in arrays.items():
+            np.save(os.path.join(a.dump_outputs, name + ".npy"), torch.stack(rows).float().cpu().numpy())
 
     # the collective of the head-parallel path: RCCL's all-reduce is the measured contract (north_star); the library's one-shot
     # all-reduce over peer-mapped buffers (clusterfusion_amd.tp.OneShotReducer) runs as a second leg
@@ -742,9 +762,10 @@ def main():
         pass
     host_issue_s = [0.0]
 
-    def timed_leg(reduce_fn, step_fn=None, health=None):
+    def timed_leg(reduce_fn, step_fn=None, health=None, after_steps=None):
         """warm-up, then EXACTLY a.steps steps between barrier + synchronize on both sides; max over ranks.  `health`: checked on
-        every rank after the first step (a collective that starts timing out -- 2 s per call -- must not eat the run)."""
+        every rank after the first step (a collective that starts timing out -- 2 s per call -- must not eat the run).
+        `after_steps`: called once the timed steps are complete, before anything else touches their outputs."""
         step = step_fn if step_fn is not None else make_step(reduce_fn)
         graph = None
         step()                      # first call: lazy init (workspace, RCCL channels)
@@ -790,6 +811,8 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         ev_ms = ev0.elapsed_time(ev1)
+        if after_steps is not None:
+            after_steps()
         # the collective alone (every rank takes part): eager back-to-back calls on one layer's output, HIP events on the stream
         coll_us = None
         if reduce_fn is not None:
@@ -927,7 +950,7 @@ def main():
             buf = torch.empty_like(outs[0])
             parity = {"collective": "RCCL all_reduce",
                       **tp_parity(l0, full[0], buf, rccl if use_dist else (lambda o: o), use_dist, rank, world, dev)}
-        dt, ev_ms, coll_us, graphed = timed_leg(rccl if use_dist else None)
+        dt, ev_ms, coll_us, graphed = timed_leg(rccl if use_dist else None, after_steps=dump_outputs if new_kv is not None else None)
         host_issue_us = host_issue_s[0] / a.steps * 1e6      # (of the headline leg: the optional legs below overwrite the cell)
 
         # per-kernel durations: HIP events recorded by the library on ITS launch stream around each
